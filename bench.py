@@ -3,7 +3,7 @@
 conjugate updates/s of batched NormalInverseWishart.ss_update (batch = 1e6, D = 16, fp64, lr = 1, default priors).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload niw|mnw_fwd|mnw_bwd|lds|dmbd]
-                    [--scaling weak|strong] [--batch B] [--dim D] [--dtype f64|f32] [--lr LR]
+                    [--scaling weak|strong] [--batch B] [--dim D] [--dtype f64|f32] [--lr LR] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over the whole synthetic batch through the product classes (-> libvbmp_hip.so),
 inputs already resident in HBM.  Workloads (BASELINE.json configs):
@@ -20,6 +20,9 @@ JSON line.  --scaling weak (default): the per-GPU batch is fixed; strong: the ba
 contiguous slices.  Independent posteriors / messages need no data-path collective; dmbd (and lds at N > 1) exchange
 their packed statistics through torch.distributed (backend nccl = RCCL over xGMI).
 Rank 0 prints ONE JSON line (metric/value/... + roofline + cpu_baseline).
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step computed (the arrays a caller of the path
+receives, its own share at N > 1) as DIR/<name>.npy, float32 / float64, at most 64 MB in all; a larger output is cut to the
+same seeded sample of units (updates / messages / series) in every array, whose indices go to DIR/sample_index.npy.
 """
 import argparse
 import json
@@ -46,6 +49,40 @@ def algorithmic_bytes_per_update(D, itemsize, lr):
     if lr != 1.0:
         elems += D * D + D + 2
     return elems * itemsize
+
+
+DUMP_BUDGET_BYTES = 64_000_000  # the files, .npy headers included
+
+
+def dump_outputs(outputs, units, path, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: outputs = {name: (tensor, axis)}, axis = the tensor's unit axis (of length `units`: updates / messages /
+    series) or None.  Every array is written as <path>/<name>.npy, float64 as float64, other floating dtypes as float32, the
+    rest as float64.  When the whole would exceed `budget` bytes, every array with a unit axis keeps the same seeded sample of
+    units along it, in ascending order, and the sample's indices are written as sample_index.npy."""
+    import numpy as np
+
+    def itemsize(t):
+        return 4 if t.is_floating_point() and t.dtype != torch.float64 else 8
+
+    outputs = {k: (v.detach(), ax if ax is not None and v.ndim > ax and v.shape[ax] == units else None)
+               for k, (v, ax) in outputs.items()}
+    total = sum(v.numel() * itemsize(v) for v, ax in outputs.values())
+    idx = None
+    if total > budget:
+        fixed = sum(v.numel() * itemsize(v) for v, ax in outputs.values() if ax is None)
+        per_unit = sum(v.numel() // units * itemsize(v) for v, ax in outputs.values() if ax is not None)
+        headers = 256 * (len(outputs) + 1)  # room for one .npy header per file (128 bytes at these ranks), the index file included
+        k = (budget - fixed - headers) // (per_unit + 8)  # + 8: the sample index itself
+        assert k >= 1, f"the outputs do not fit {budget} bytes even with one unit"
+        idx = torch.randperm(units, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+    os.makedirs(path, exist_ok=True)
+    for name, (v, ax) in outputs.items():
+        if idx is not None and ax is not None:
+            v = v.index_select(ax, idx.to(v.device))
+        v = v.to(torch.float32 if itemsize(v) == 4 else torch.float64)
+        np.save(os.path.join(path, name + ".npy"), v.contiguous().cpu().numpy())
+    if idx is not None:
+        np.save(os.path.join(path, "sample_index.npy"), idx.to(torch.float64).numpy())
 
 
 def make_inputs(B, D, dtype, device, n=32, seed=0):
@@ -105,6 +142,7 @@ class NiwWorkload:
         a = self.a
         self.B = B = _local_count(a.batch, rank, world, scaling)
         self.SExx, self.SEx, self.N = make_inputs(B, a.dim, self.dtype, device, seed=rank)
+        torch.manual_seed(rank)  # the posterior's random initial mean (blended in when lr < 1)
         self.q = NormalInverseWishart((a.dim,), (B,), device=device, dtype=self.dtype)
         self.units = B
         self.bpu = algorithmic_bytes_per_update(a.dim, 8 if self.dtype == torch.float64 else 4, a.lr)
@@ -113,6 +151,11 @@ class NiwWorkload:
 
     def step(self):
         self.q.ss_update(self.SExx, self.SEx, self.N, lr=self.a.lr, beta=None)
+
+    def outputs(self):
+        q = self.q
+        return {"lambda_mu": (q.lambda_mu, 0), "mu": (q.mu, 0), "invU": (q.invU.invU, 0), "U": (q.invU.U, 0),
+                "nu": (q.invU.nu, 0), "logdet_invU": (q.invU.logdet_invU, 0)}, self.B
 
     def config(self, world, scaling):
         a = self.a
@@ -211,6 +254,13 @@ class MnwMessageWorkload:
         else:
             self.out = self.m.backward(self.msg)
 
+    def outputs(self):
+        px, res = self.out
+        if self.dir == "forward":
+            return {"mu": (px.mu, 0), "Sigma": (px.Sigma, 0), "Res": (res, 0)}, self.N
+        return {"invSigma": (px.invSigma, 0), "invSigmamu": (px.invSigmamu, 0), "logdetinvSigma": (px.logdetinvSigma, 0),
+                "Res": (res, 0)}, self.N
+
     def config(self, world, scaling):
         per = "per GPU" if scaling == "weak" else "in total"
         return {"workload": f"BASELINE configs[2]: MatrixNormalWishart.{self.dir}, {self.total} messages {per}, one precision "
@@ -292,6 +342,15 @@ class LdsWorkload:
         m.update_latents(*self.inputs)
         if self.world > 1:
             m.reduce_statistics()  # the E-step's statistics cross the ranks in ONE packed all-reduce
+
+    def outputs(self):
+        """the smoothed posteriors (time first, series second), logZ and the time-integrated statistics per series"""
+        m = self.m
+        out = {"px_" + f: (getattr(m.px, f), 1) for f in ("mu", "Sigma", "invSigma", "invSigmamu")}
+        out["logZ"] = (m.logZ, 0)
+        for f in ("SE_x_x", "SE_x0_x0", "SE_x0", "SE_y_xr", "SE_y_y", "SE_xpu_xpu", "SE_x_xpu", "SE_xr_xr"):
+            out[f] = (getattr(m, f), 0)
+        return out, self.S
 
     def config(self, world, scaling):
         per = "per GPU" if scaling == "weak" else "in total"
@@ -383,6 +442,13 @@ class DmbdWorkload:
         # --graphed: the iteration replayed as one HIP graph (single rank only: the collectives are not captured)
         self.m.update(self.y, None, None, iters=1, latent_iters=1, lr=self.a.dmbd_lr, graphed=self.a.graphed and self.reducer is None)
         self.iterations += 1
+
+    def outputs(self):
+        """the iteration's ELBO, the role assignment probabilities and the smoothed latent posteriors (time first, series second)"""
+        m = self.m
+        out = {"ELBO": (m.ELBO_last.reshape(-1), None), "assignment_pr": (m.assignment_pr(), 1)}
+        out.update({"px_" + f: (getattr(m.px, f), 1) for f in ("mu", "Sigma", "invSigma", "invSigmamu")})
+        return out, self.S
 
     def config(self, world, scaling):
         per = "per GPU" if scaling == "weak" else "in total"
@@ -505,6 +571,8 @@ def main():
     ap.add_argument("--graphed", action="store_true", help="dmbd: replay the VB iteration as one HIP graph (pyvbmp_amd.graph)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-strong", action="store_true", dest="no_strong", help="N > 1: skip the extra strong-scaling pass")
+    ap.add_argument("--dump-outputs", default=None, dest="dump_outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0's share, at most 64 MB)")
     args = ap.parse_args()
     args.batch_set, args.dim_set, args.dtype_set = args.batch, args.dim, args.dtype
     if args.batch is None:
@@ -516,6 +584,8 @@ def main():
     ds, dw = DEFAULT_STEPS[args.workload]
     args.steps = ds if args.steps is None else args.steps
     args.warmup = dw if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)
@@ -605,6 +675,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     _lib.launch_hooks = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(*wl.outputs(), args.dump_outputs)
     kernel_ms_source = "HIP events around each launch inside the timed region"
     if args.graphed and args.workload == "dmbd" and world == 1 and not starts:
         # a graph replay launches nothing from Python, so no hook fires: the dominant kernel's duration is measured on three

@@ -11,6 +11,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -99,10 +100,12 @@ def test_bench_under_torch_distributed_run():
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("workload,extra", [("niw", ["--batch", "100000"]), ("mnw_fwd", ["--batch", "8192"]), ("mnw_bwd", ["--batch", "8192"]),
                                             ("lds", ["--batch", "256", "--T", "100"]), ("dmbd", ["--batch", "4"])])
-def test_bench_workloads_emit_the_contract_line(workload, extra):
+def test_bench_workloads_emit_the_contract_line(workload, extra, tmp_path):
     """every workload of bench.py on one GPU (small sizes): ONE JSON line with the contract's keys, a roofline object whose
-    numbers are consistent with each other, and a cpu_baseline"""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "3", "--warmup", "1"] + extra
+    numbers are consistent with each other, and a cpu_baseline; --dump-outputs leaves float32 / float64 arrays, 64 MB at most"""
+    dump = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(dump)] + extra
     r = subprocess.run(cmd, env=_plain_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -125,6 +128,31 @@ def test_bench_workloads_emit_the_contract_line(workload, extra):
     else:
         cb = out["cpu_baseline"]
         assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["unit"] == out["unit"] and cb["sample"]
+    arrays = {f: np.load(dump / f) for f in os.listdir(dump)}
+    assert arrays and all(f.endswith(".npy") for f in arrays)
+    assert all(a.dtype in (np.float32, np.float64) and a.size > 0 for a in arrays.values())
+    assert sum(os.path.getsize(dump / f) for f in arrays) <= 64_000_000
+
+
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_repeat_exactly(tmp_path):
+    """two runs with the same arguments dump the same arrays (the batch is larger than the dump: a seeded sample of it)"""
+    outs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "100000", "--steps", "2", "--warmup", "1",
+               "--no-cpu-baseline", "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, env=_plain_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=500)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        outs.append(tmp_path / run)
+    files = sorted(os.listdir(outs[0]))
+    assert files == sorted(os.listdir(outs[1]))
+    assert {"mu.npy", "invU.npy", "U.npy", "logdet_invU.npy", "sample_index.npy"} <= set(files)
+    assert len(np.load(outs[0] / "sample_index.npy")) < 100000
+    for f in files:
+        a, b = np.load(outs[0] / f), np.load(outs[1] / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
 
 
 @pytest.mark.timeout(600)
