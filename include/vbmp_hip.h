@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define VBMP_ABI_VERSION 8
+#define VBMP_ABI_VERSION 9
 int vbmp_abi_version(void);
 
 /* K1 -- Ainv = A^-1 and logdet = log det A of B symmetric positive definite matrices.
@@ -270,6 +270,22 @@ int vbmp_hmm_forward_backward_f64(const double* logits, const double* trans, con
 int vbmp_hmm_forward_backward_f32(const float* logits, const float* trans, const float* init, int64_t Tn, int64_t C,
                                   int64_t NB, int K, float ptemp, float* p, float* SEzz, float* SEz0, float* logZ,
                                   void* stream);
+
+/* K16 -- forward-backward of an input-driven HMM (dHMM.forward_backward_loop, models/dHMM.py:42-78): the transition
+ * matrix changes at every step.  C independent chains of length Tn over K states; chain c uses the initial
+ * distribution of batch element c % NB.  obs (Tn,C,K): observation log-likelihoods; tr (Tn,C,K,K): transition logits
+ * of every step (row = from, column = to; -inf = forbidden; step 0 leaves a virtual state drawn from init);
+ * init (NB,K): E log initial.  Outputs dense: p (Tn,C,K) = softmax of the smoothed messages with temperature ptemp,
+ * SEzz (Tn,C,K,K) = pair posterior of every step (NOT summed over time; slot 0 pairs the virtual state with step 0),
+ * SEz0 (C,K) = posterior of the virtual state, logZ (C).  NaN where the reference's log-sum-exp meets an all -inf set.
+ * 1 <= K <= VBMP_DHMM_MAX_K; Tn = 0 or C = 0 is empty work (returns 0). */
+#define VBMP_DHMM_MAX_K 64
+int vbmp_dhmm_forward_backward_f64(const double* obs, const double* tr, const double* init, int64_t Tn, int64_t C,
+                                   int64_t NB, int K, double ptemp, double* p, double* SEzz, double* SEz0, double* logZ,
+                                   void* stream);
+int vbmp_dhmm_forward_backward_f32(const float* obs, const float* tr, const float* init, int64_t Tn, int64_t C,
+                                   int64_t NB, int K, float ptemp, float* p, float* SEzz, float* SEz0, float* logZ,
+                                   void* stream);
 
 /* K5b -- streaming weighted sum of per-sample matrices: out[e] += sum_{s<S} w[s] * C[s,e], e < E (= d*d): the
  * covariance part of MatrixNormalWishart.update (sum_s p_s Sigma_s, transforms/MatrixNormalWishart.py:153-155).

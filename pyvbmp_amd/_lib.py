@@ -17,7 +17,7 @@ _c_int = ctypes.c_int
 _c_ptr = ctypes.c_void_p
 _c_double = ctypes.c_double
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _lib = None
 
@@ -109,6 +109,14 @@ def _sig_hmm(T):
 HMM_MAX_K = 64
 
 
+def _sig_dhmm(T):
+    # obs, tr, init, Tn, C, NB, K, ptemp, p, SEzz, SEz0, logZ, stream
+    return [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, T, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr]
+
+
+DHMM_MAX_K = 64
+
+
 def _sig_matsum(T):
     # C, w, S, E, out, stream
     return [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr]
@@ -141,6 +149,7 @@ SYMBOLS = {
     # ... + res_w (host, 8 values), res_c, res, add_cvec before the stream
     "vbmp_mnw_message_res": lambda T: _sig_mnw_msg(T)[:-1] + [_c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr],
     "vbmp_hmm_forward_backward": _sig_hmm,
+    "vbmp_dhmm_forward_backward": _sig_dhmm,
     "vbmp_weighted_matsum": _sig_matsum,
     "vbmp_weighted_matsum_cols": _sig_matsum_cols,
     "vbmp_rows_affine": _sig_rows,
@@ -240,7 +249,7 @@ def call(fn, name, *args):
 def check(rc, name):
     if rc != 0:
         why = {-1: "bad argument: a null pointer, a negative size, or a size beyond the kernel's limit -- matrices D <= 64 "
-                   "(K1 / K2 / K3a), message dims <= 32 (K7 / K8), <= 64 states (K11), <= 64 row entries (K12), <= 65535 "
+                   "(K1 / K2 / K3a), message dims <= 32 (K7 / K8), <= 64 states (K11, K16), <= 64 row entries (K12), <= 65535 "
                    "experts / components per launch; see INTEGRATION.md, section Limits",
                -2: "HIP launch failure"}.get(rc, "unknown")
         raise VbmpHipError(f"{name} failed with code {rc} ({why})")

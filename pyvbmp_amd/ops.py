@@ -558,6 +558,34 @@ def hmm_forward_backward(logits, trans, init, batch_shape, ptemp=1.0):
     return p, SEzz, SEz0, logZ
 
 
+def dhmm_forward_backward(obs, tr, init, batch_shape, ptemp=1.0):
+    """K16: forward-backward with a transition matrix per (time step, chain) (ref models/dHMM.py:42-78).
+    obs: (T,)+sample+batch+(K,); tr: broadcastable to (T,)+sample+batch+(K,K) (row = from, column = to); init: batch+(K,).
+    Returns p (T,)+sample+batch+(K,), SEzz (T,)+sample+batch+(K,K) (not summed over time), SEz0 sample+batch+(K,),
+    logZ sample+batch."""
+    dev = L.require_device(obs, tr, init)
+    lib = L.load()
+    dt = obs.dtype
+    K = obs.shape[-1]
+    T = obs.shape[0]
+    lead = tuple(obs.shape[1:-1])
+    C, NB = _prod(lead), _prod(batch_shape)
+    ob = obs.contiguous()
+    trc = tr.to(dt).expand((T,) + lead + (K, K)).contiguous()
+    ini = init.to(dt).expand(tuple(batch_shape) + (K,)).contiguous()
+    p = torch.empty_like(ob)
+    SEzz = torch.empty((T,) + lead + (K, K), dtype=dt, device=dev)
+    SEz0 = torch.empty(lead + (K,), dtype=dt, device=dev)
+    logZ = torch.empty(lead, dtype=dt, device=dev)
+    if C > 0 and T > 0:
+        suf = L.suffix(dt)
+        fn = getattr(lib, "vbmp_dhmm_forward_backward_" + suf)
+        cT = L.DTYPES[suf][1]
+        L.call(fn, "vbmp_dhmm_forward_backward", L.ptr(ob), L.ptr(trc), L.ptr(ini), T, C, max(NB, 1), K, cT(float(ptemp)),
+               L.ptr(p), L.ptr(SEzz), L.ptr(SEz0), L.ptr(logZ), L.stream_ptr(dev))
+    return p, SEzz, SEz0, logZ
+
+
 def weighted_matsum(C, w=None):
     """K5b: sum_s w[s] * C[s] for C (S, ...) dense and w (S,) or None; returns C.shape[1:]."""
     dev = L.require_device(C, w)

@@ -304,6 +304,83 @@ def bench_gmm(args):
                   f"-> {N / t_it * 1e3:.3e} samples/s", flush=True)
 
 
+def _dhmm_composed(obs, tr, init, ptemp=1.0):
+    """The reference's recursion (models/dHMM.py:42-78) composed from torch ops on the device -- a host loop over T with
+    a few launches per step: the baseline K16 replaces"""
+    def lse(x, dims, keepdim=False):
+        m = x.amax(dims, keepdim=True)
+        return m.amax(dims, keepdim) + (x - m).exp().sum(dim=dims, keepdim=keepdim).log()
+    f = obs.clone()
+    f[0] = lse(obs[0].unsqueeze(-2) + init.unsqueeze(-1) + tr[0], -2)
+    for t in range(1, obs.shape[0]):
+        f[t] = lse(f[t - 1].unsqueeze(-1) + obs[t].unsqueeze(-2) + tr[t], -2)
+    logZ = lse(f[-1], -1, True)
+    f = f - logZ
+    SEzz = torch.zeros(tuple(f.shape) + (f.shape[-1],), dtype=f.dtype, device=f.device)
+    for t in range(obs.shape[0] - 2, -1, -1):
+        a = f[t].unsqueeze(-1) + tr[t + 1]
+        xi = (a - lse(a, -2, True)) + f[t + 1].unsqueeze(-2)
+        f[t] = lse(xi, -1)
+        SEzz[t + 1] = (xi - lse(xi, (-1, -2), True)).exp()
+    a = init.unsqueeze(-1) + tr[0]
+    xi = (a - lse(a, -2, True)) + f[0].unsqueeze(-2)
+    s0 = lse(xi, -1)
+    SEz0 = (s0 - lse(s0, -1, True)).exp()
+    SEzz[0] = (xi - lse(xi, (-1, -2), True)).exp()
+    p = torch.softmax((f - f.max(-1, keepdim=True)[0]) / ptemp, -1)
+    return p, SEzz, SEz0, logZ.squeeze(-1)
+
+
+def bench_dhmm(args):
+    """K16 (driven-HMM forward-backward) alone at T=1000, C=4096 chains, K = 8 and 25, fp64 / fp32, against its algorithmic
+    bytes T*C*(2K^2 + 2K)*itemsize (obs and tr read once, p and SEzz written once); then one full dHMM.raw_update iteration
+    (T=1000, 4096 series, K=8, p=10, obs dim 2) split into phases, and the recursion composed from torch ops as baseline."""
+    T, C = args.T, args.S
+    for K in (() if args.dhmm_model_only else (8, 25)):
+        for dt in (torch.float64, torch.float32):
+            g = torch.Generator(device="cuda").manual_seed(K)
+            es = torch.finfo(dt).bits // 8
+            obs = 2.0 * torch.randn(T, C, K, generator=g, device="cuda", dtype=dt)
+            tr = torch.randn(T, C, K, K, generator=g, device="cuda", dtype=dt).mul_(1.5)
+            init = torch.log_softmax(torch.randn(K, generator=g, device="cuda", dtype=dt), -1)
+            mean, best, med = timed(lambda: ops.dhmm_forward_backward(obs, tr, init, ()), reps=max(3, args.reps // 6))
+            byt = T * C * (2 * K * K + 2 * K) * es
+            print(f"dhmm K16 {str(dt)[6:]} T={T} C={C} K={K}: {med:.3f} ms (min {best:.3f})  {byt / 1e6:.0f} MB -> "
+                  f"{byt / med / 1e6:.0f} GB/s = {byt / med / 1e6 / 80:.1f}% of 8 TB/s  ({med / T * 1e3:.2f} us/step)", flush=True)
+            if K == 8:
+                t_c = _time_call(lambda: _dhmm_composed(obs, tr, init), reps=3, warm=1)
+                print(f"dhmm composed torch-op recursion {str(dt)[6:]} K={K}: {t_c:.1f} ms -> K16 {t_c / med:.1f}x", flush=True)
+            del obs, tr
+            torch.cuda.empty_cache()
+    from pyvbmp_amd.dists import NormalInverseWishart
+    from pyvbmp_amd.models import dHMM
+    K, p, d = 8, 10, 2
+    for dt in (torch.float64, torch.float32):
+        g = torch.Generator(device="cuda").manual_seed(1)
+        X = torch.randn(T, C, p, generator=g, device="cuda", dtype=dt)
+        z = ((X[..., :3] > 0).long() * torch.tensor([1, 2, 4], device="cuda")).sum(-1)
+        B = 2.0 * torch.randn(K, d, generator=g, device="cuda", dtype=dt)
+        Y = B[z] + 0.1 * torch.randn(T, C, d, generator=g, device="cuda", dtype=dt)
+        m = dHMM(NormalInverseWishart((d,), (K,), device="cuda", dtype=dt), p)
+        m.raw_update(X, Y, iters=1)
+        Xu, Yu = X.unsqueeze(-2), Y.unsqueeze(-2)
+        t_it = _time_call(lambda: m.raw_update(X, Y, iters=1), reps=3)
+        t_obs = _time_call(lambda: m.obs_logits(Yu), reps=3)
+        t_tr = _time_call(lambda: m.transition_logits(Xu), reps=3)
+        ol, tl = m.obs_logits(Yu), m.transition_logits(Xu)
+        t_fb = _time_call(lambda: m.forward_backward_loop(ol, tl), reps=3)
+        m.raw_update_states(Xu, Yu)
+        t_mn = _time_call(lambda: m.transition.raw_update(Xu, m.SEzz, iters=4), reps=3)
+        t_niw = _time_call(lambda: m.raw_update_obs_parms(Yu), reps=3)
+        t_c = _time_call(lambda: _dhmm_composed(ol, tl, m.initial.loggeomean()), reps=3, warm=1)
+        t_base = t_it - t_fb + t_c
+        print(f"dhmm raw_update {str(dt)[6:]} T={T} series={C} K={K} p={p} obs={d}: iteration {t_it:.1f} ms  [obs logits {t_obs:.1f}, "
+              f"transition logits {t_tr:.1f}, K16 {t_fb:.1f}, MNLR update {t_mn:.1f}, NIW update {t_niw:.1f}]; with the composed "
+              f"recursion ({t_c:.1f} ms) {t_base:.1f} ms -> {t_base / t_it:.1f}x end to end", flush=True)
+        del m, X, Y, ol, tl
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["niw"])
@@ -312,6 +389,7 @@ if __name__ == "__main__":
     ap.add_argument("--N", type=int, default=262144)
     ap.add_argument("--T", type=int, default=1000)
     ap.add_argument("--S", type=int, default=4096)
+    ap.add_argument("--dhmm-model-only", action="store_true", help="dhmm: skip the kernel-only part")
     args = ap.parse_args()
     for w in args.what:
-        {"niw": bench_niw, "copy": bench_copy, "mnw": bench_mnw, "lds": bench_lds, "dmbd": bench_dmbd, "gmm": bench_gmm, "gmm0": bench_gmm0, "lds0": bench_lds0, "mixlt": bench_mixlt, "dmix": bench_dmix, "k1": bench_k1}[w](args)
+        {"niw": bench_niw, "copy": bench_copy, "mnw": bench_mnw, "lds": bench_lds, "dmbd": bench_dmbd, "gmm": bench_gmm, "gmm0": bench_gmm0, "lds0": bench_lds0, "mixlt": bench_mixlt, "dmix": bench_dmix, "k1": bench_k1, "dhmm": bench_dhmm}[w](args)
